@@ -31,10 +31,12 @@ every rank a 512-trajectory batch of its own; --emulate-world W times one rank's
 W-rank job on one GPU (collectives excluded).
 
 Every hot kernel is timed live with HIP events on its launch stream (the dominant one feeds
-`roofline`). After the timed steps, the advantage + loss kernels (56 B/token)
-are replayed from a HIP graph at the batch size and at 16x it (`advantage_loss`). The CPU
-oracle (oracle/cpu_ref.py + oracle/sampler_ref.c, "port") is timed on a bounded sample on
-rank 0 at N=1.
+`roofline`). A plain run sets up, warms up, times --steps steps, writes the last step's outputs
+(--dump-outputs DIR) and prints the result line. With --full the side legs run after the timed
+steps: the advantage + loss kernels (56 B/token) replayed from a HIP graph at the
+batch size and at 16x it (`advantage_loss`), the rollout attention, lm_head, filtered-sampler and
+per-vocabulary legs, the CPU oracle (oracle/cpu_ref.py + oracle/sampler_ref.c, "port") timed on
+a bounded sample on rank 0 at N=1, and the real-model `end_to_end` child.
 """
 
 from __future__ import annotations
@@ -230,10 +232,11 @@ def run(args):
     n_params = -(-args.params // emulate)  # an emulated rank's shard (the real layout pads to 64 x W)
     if args.params > 0:
         reducer = comm.GradReducer(n_params, dev, bucket_bytes=args.bucket_mb << 20)
-        init = torch.empty(n_params, dtype=torch.float32, device=dev).normal_(0.0, 0.02)
+        pgen = torch.Generator(device=dev).manual_seed(4321)  # seeded: the same inputs in every run
+        init = torch.empty(n_params, dtype=torch.float32, device=dev).normal_(0.0, 0.02, generator=pgen)
         opt = comm.ShardedAdamW(reducer, init, comm.AdamWConfig())
         del init
-        reducer.grad.normal_(0.0, 1e-3)
+        reducer.grad.normal_(0.0, 1e-3, generator=pgen)
         torch.cuda.synchronize()
     upd_done = None  # inflight: the comm stream's update of the previous step
 
@@ -305,6 +308,7 @@ def run(args):
     metrics_acc = torch.zeros(8, dtype=torch.float32, device=dev)
     grpo_timer, plan_timer, fold_timer = KernelTimer(), KernelTimer(), KernelTimer()
     timers = timers + (grpo_timer, plan_timer, fold_timer)
+    last = {}  # --dump-outputs: the tensors a step allocates itself (see dump_outputs)
 
     def step(step_idx):
         nonlocal upd_done
@@ -401,6 +405,10 @@ def run(args):
             else:
                 adam_timer.wrap(lambda: opt.step(n_micro=N // mb, zero_grad=False))
                 opt.sync_weights()
+        if args.dump_outputs:  # this step's per-step tensors, kept until the next step replaces them
+            last.update(sequences=seqs, attention_mask=att, response_mask=rmask, rewards=rew, loss_mask=lmask,
+                        rollout_logprobs=rlp, loss_mask_row_sums=lrows, scores=scores, ref_logprobs=ref_lp,
+                        old_logprobs=old_lp, advantages=adv)
         return metrics_acc
 
     for w in range(args.warmup):
@@ -431,6 +439,20 @@ def run(args):
     elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
     value = N * world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        outs = dict(last, rollout_tokens=sampler.tokens, rollout_token_logprobs=sampler.logprobs, metrics=m,
+                    dlogits_last_micro_batch=dlogits)
+        if args.rollout == "live":  # a slot past the live count of its decode step was never sampled
+            dead = torch.arange(N, device=dev)[None] >= torch.tensor(live, device=dev)[:, None]
+            outs["rollout_tokens"] = sampler.tokens.masked_fill(dead, 0)
+            outs["rollout_token_logprobs"] = sampler.logprobs.masked_fill(dead, 0.0)
+        if args.unfused:
+            outs.update(logprobs_last_micro_batch=lp, entropy_last_micro_batch=ent)
+        else:
+            outs.update(logprobs=step_lp, entropy=step_ent, micro_batch_loss=step_loss, micro_batch_metrics=step_met)
+        if opt is not None:
+            outs.update(grad_norm=opt.grad_norm, master_weights=opt.param, rollout_weights_bf16=opt.weights_bf16)
+        dump_outputs(args.dump_outputs, outs)
 
     # per-kernel roofline: algorithmic bytes per launch / average event-timed launch duration
     rows_per_launch = mb * R
@@ -541,7 +563,8 @@ def run(args):
             "note": "one process running one rank's share of a strong-scaling job: its rows and its 1/W "
                     "optimizer shard, no reduce-scatter / all-gather / metric all-reduce (collectives excluded)",
             "projected_value_excluding_collectives": round(N_GLOBAL * args.steps / elapsed, 3)}
-    legs = rank == 0  # the single-GPU legs after the timed region: rank 0 only; the others wait at the barrier
+    # the single-GPU legs after the timed region (--full only): rank 0 only; the others wait at the barrier
+    legs = rank == 0 and args.full
     NL = PROMPTS * GROUP  # the legs keep the headline shape (512 trajectories) at every world size
     if legs and not args.no_adv_loss_leg:
         result["advantage_loss"] = {"batch": advantage_loss_leg(dev, NL, R, variants=args.adv_loss_variants),
@@ -555,9 +578,9 @@ def run(args):
         result["sampler_filtered"] = sampler_filtered_leg(dev, NL, V)
     if legs and not args.no_vocab_legs:
         result["policy_train_vocabs"] = policy_train_vocab_legs(dev, mb, R)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if legs and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args)
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if legs and world == 1 and not args.no_e2e:
         del logits, dlogits, reducer, opt  # the real-model leg needs the HBM the resident logits hold
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -567,6 +590,33 @@ def run(args):
     if dist_on:
         dist.barrier()  # every rank leaves together (rank 0 ran the legs)
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of an output larger than this
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tensors):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per
+    tensor in float32 (token ids, masks and bf16 values are exact in it). An output of more than
+    DUMP_SAMPLE elements (the micro-batch's dlogits, the weights) is written as a fixed sample:
+    DUMP_SAMPLE flat indices drawn once from torch.Generator seed 99, the same in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(tensors.items()):
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(99)
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).to(t.device)
+            t = t.reshape(-1)[idx]  # (the large outputs are contiguous: a view)
+        a = t.to(torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_CAP_BYTES:
+            raise RuntimeError(f"--dump-outputs would write more than {DUMP_CAP_BYTES} bytes at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"wrote {len(tensors)} arrays ({total / 2**20:.1f} MiB) to {out_dir}")
 
 
 def end_to_end_leg(timeout_s=900):
@@ -1120,6 +1170,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--micro-batch", type=int, default=16)
     ap.add_argument("--logits-rows", type=int, default=0, help="0 = the whole batch if HBM allows")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs (graph-replayed advantage+loss, rollout "
+                         "attention, lm_head, filtered sampler, per-vocabulary passes, CPU baseline, real-model "
+                         "end-to-end step); each has a --no-* switch. Without --full none of them runs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the real-model end-to-end leg (N=1 only)")
     ap.add_argument("--no-adv-loss-leg", action="store_true", help="skip the graph-replayed advantage+loss leg")

@@ -8,7 +8,7 @@
 #   tests[:EXPR]   pytest -m gpu (optionally -k EXPR), -x, per-test 120 s limit
 #   files:F1,F2    pytest -m gpu on the given test files only
 #   smoke          __graft_entry__.smoke()
-#   bench          python bench.py (the driver's default run)
+#   bench          python bench.py --full (the timed steps and every side leg)
 #   emu8           bench.py --emulate-world 8 (one rank's share of an 8-GPU job), no side legs
 #   prof           rocprofv3 --kernel-trace --stats of a short bench run (N = 1)
 #   prof_emu8      the same for the emu8 run
@@ -49,7 +49,7 @@ for S in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O.log 2>&1
       rc=$?; tail -2 $O.log; step_rc smoke $rc $O.log ;;
     bench)
-      timeout -k 10 600 python -u bench.py > $O.json 2> $O.err
+      timeout -k 10 600 python -u bench.py --full > $O.json 2> $O.err
       rc=$?; tail -c 400 $O.json; echo; step_rc bench $rc $O.err ;;
     emu8)
       timeout -k 10 400 python -u bench.py --emulate-world 8 $NOLEGS > $O.json 2> $O.err

@@ -43,6 +43,48 @@ def test_pmc_traffic_lookup_matches_committed_profile():
     assert bench.pmc_traffic("no_such_kernel", 0) is None
 
 
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample_of_large_ones(tmp_path):
+    """--dump-outputs: one float32 .npy per output, exact for token ids / bf16, a large output as
+    the same DUMP_SAMPLE seeded elements in every run, and never more than the 64 MB cap."""
+    import numpy as np
+    import pytest
+    import torch
+
+    big = torch.arange(bench.DUMP_SAMPLE + 7, dtype=torch.int32).reshape(-1, 1)
+    outs = {"tokens": torch.tensor([[151935, 0], [7, 2 ** 24]], dtype=torch.int32),
+            "w": torch.tensor([0.5, -3.0], dtype=torch.bfloat16), "big": big}
+    a, b = str(tmp_path / "a"), str(tmp_path / "b" / "nested")
+    bench.dump_outputs(a, outs)
+    bench.dump_outputs(b, outs)
+    assert sorted(os.listdir(a)) == ["big.npy", "tokens.npy", "w.npy"]
+    for name in outs:
+        x, y = np.load(os.path.join(a, name + ".npy")), np.load(os.path.join(b, name + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert np.array_equal(np.load(os.path.join(a, "tokens.npy")), [[151935, 0], [7, 2 ** 24]])
+    assert np.array_equal(np.load(os.path.join(a, "w.npy")), [0.5, -3.0])
+    s = np.load(os.path.join(a, "big.npy"))
+    assert s.shape == (bench.DUMP_SAMPLE,) and len(np.unique(s)) > bench.DUMP_SAMPLE // 2
+    assert s.min() >= 0 and s.max() < big.numel()
+    assert bench.DUMP_CAP_BYTES == 64 << 20
+    with pytest.raises(RuntimeError):  # 17 sampled outputs x 4 MiB > 64 MiB
+        bench.dump_outputs(str(tmp_path / "c"), {f"o{i}": big for i in range(17)})
+
+
+def test_plain_run_has_no_side_legs_unless_full():
+    """The plain run's argument defaults: --full off (no side legs), no output dump."""
+    import sys
+    from unittest import mock
+
+    seen = {}
+    with mock.patch.object(bench, "run", lambda a: seen.update(vars(a))):
+        with mock.patch.object(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]):
+            bench.main()
+        assert seen["full"] is False and seen["dump_outputs"] is None and (seen["steps"], seen["warmup"]) == (7, 2)
+        with mock.patch.object(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"]):
+            bench.main()
+        assert seen["full"] is True and seen["dump_outputs"] == "d"
+
+
 def _dry(gpus):
     import subprocess
     import sys
